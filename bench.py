@@ -15,10 +15,18 @@ planners are sharded across ranks with no data-path collective -> weak scaling.
 torch.distributed.run with N ranks as a child process (before anything touches a GPU) and
 exits with its status.
 
-Extra fields: the first (cold: no longest-first history) step's throughput, plan latency of
-single queries on the GPU and on one CPU core for the SAME queries, the search kernel's
-roofline (SURVEY.md §8d algorithmic bytes / kernel time from HIP events on its stream), and
-the CPU oracle timed on `cores` host threads, one private planner per thread (rank 0).
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up (the first warm-up step
+is the cold one: no longest-first history), times the K steps and prints the result line:
+`value`, `ms_per_step` and what the timed steps themselves yield (per-step kernel times, the
+step's balance, the search kernel's roofline: SURVEY.md §8d algorithmic bytes / kernel time from
+HIP events on its stream).  `--dump-outputs DIR` also writes what the last timed step returned
+(dump_outputs).
+
+`--full` adds, after the timed steps, every other leg to the same line: a cold-order step, plan
+latency of single queries on the GPU and on one CPU core for the SAME queries, the relaxed mode,
+velocity profiles, the bit-exact parity sample against the oracle, and the CPU oracle timed on
+`cores` host threads, one private planner per thread (rank 0); for cfg4 the map build and the
+heuristic field, local and row-sharded; for cfg5 the relaxed tick and the CPU's replay.
 """
 import argparse
 import hashlib
@@ -52,6 +60,39 @@ def algorithmic_bytes(st, K):
     (st: the stats structured array of one batched call)."""
     return float(40 * st["pops"].astype(np.float64).sum() + 44 * st["successors"].astype(np.float64).sum()
                  + 208 * st["astar_pops"].astype(np.float64).sum() + 12.0 * K * len(st))
+
+
+DUMP_SEED = 0
+DUMP_MAX_POSES = 3_000_000  # 16 bytes a pose (x, y, heading, curvature): 48 MB of the 64 MB a dump may take
+
+
+def dump_outputs(dirname, res, max_poses=DUMP_MAX_POSES):
+    """`--dump-outputs DIR`: what one batched find_path returned (`res`, a BatchResult), as
+    DIR/<name>.npy in float32 / float64, for comparing two builds output for output (the inputs
+    depend on the command line alone).  Of every planner: cost, ok, path_len, the search
+    statistics that the outcome determines (stats_<field>) and the pop and closed digests (as
+    their high and low 32-bit halves: float64 holds no 64-bit integer).  Paths: the poses and
+    curvatures that the call wrote to the caller's buffers, packed one planner after the other,
+    of a fixed sample of planners: a seeded permutation of the batch, taken while the running
+    pose count stays within `max_poses`, in ascending planner order (sample_planner; planner
+    i's poses are path_len[i], capped at the buffers' capacity, rows of path_xyh)."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    st = res.stats
+    np.save(d / "cost.npy", np.asarray(res.cost, np.float32))
+    np.save(d / "ok.npy", np.asarray(res.ok, np.float32))
+    np.save(d / "path_len.npy", np.asarray(res.lens, np.float64))
+    for k in ("pops", "successors", "astar_pops", "astar_searches", "shots", "closed_size", "via_shot", "status"):
+        np.save(d / f"stats_{k}.npy", st[k].astype(np.float64))
+    for k in ("pop_digest", "closed_digest"):
+        v = st[k].astype(np.uint64)
+        np.save(d / f"stats_{k}_hi_lo.npy", np.stack([v >> np.uint64(32), v & np.uint64(0xFFFFFFFF)], 1).astype(np.float64))
+    held = np.clip(np.asarray(res.lens, np.int64), 0, res.xyh.shape[1])
+    order = np.random.default_rng(DUMP_SEED).permutation(len(held))
+    take = np.sort(order[np.cumsum(held[order]) <= max_poses])
+    np.save(d / "sample_planner.npy", take.astype(np.float64))
+    np.save(d / "path_xyh.npy", np.concatenate([res.xyh[i, :held[i]] for i in take] or [np.zeros((0, 3))]).astype(np.float32))
+    np.save(d / "path_curvature.npy", np.concatenate([res.curv[i, :held[i]] for i in take] or [np.zeros(0)]).astype(np.float32))
 
 
 def step_balance(planners):
@@ -181,6 +222,15 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=None,
                     help="timed steps (default 3; cfg5: 20 ticks, SURVEY.md §8(d)'s 20 ticks at 20 Hz)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (cold-order step, single-query latency, "
+                         "relaxed mode, velocity profiles, bit-exact parity against the oracle, CPU baseline; cfg4: "
+                         "the map build and heuristic field; cfg5: the relaxed tick and the CPU replay).  Without it "
+                         "a run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (rank 0's batch) to DIR/<name>.npy: cost, ok, "
+                         "path_len, stats_* and digests of every planner, and the packed paths of a fixed seeded "
+                         "sample of planners (dump_outputs)")
     ap.add_argument("--batch", type=int, default=int(os.environ.get("HASTAR_BENCH_BATCH", "23552")),
                     help="planners (queries) per GPU")
     ap.add_argument("--grid", type=int, default=None, help="default 1024 (cfg3, cfg5) or 2048 (cfg4)")
@@ -190,35 +240,35 @@ def parse_args(argv=None):
                     help="initial arena of a search in pops (0 = the library's 262144; default: 196608 for cfg3 "
                          "so that ~1984 arenas of 46 MiB fit next to the planners' maps, 0 otherwise)")
     ap.add_argument("--max-astar-nodes", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU-oracle baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: budget of the CPU-oracle baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the parity sample and the CPU baseline")
     ap.add_argument("--parity-all", action="store_true",
-                    help="check EVERY query's cold step against the oracle (success, cost bits, statistics, "
+                    help="implies --full: check EVERY query's cold step against the oracle (success, cost bits, statistics, "
                          "pop/closed digests; about a minute of 16 host threads at cfg3)")
     ap.add_argument("--step-diag", action="store_true",
                     help="per-step schedule diagnostics in the JSON line (reads every search's timing per step)")
-    ap.add_argument("--latency-queries", type=int, default=3)
+    ap.add_argument("--latency-queries", type=int, default=3, help="--full: single queries timed alone")
     ap.add_argument("--workload", choices=("cfg3", "cfg4", "cfg5"), default="cfg3",
                     help="cfg3: batch of independent queries (default, the headline line); "
                          "cfg4: 2048^2 queries with the map build row-sharded over the ranks + RCCL all-gather "
                          "(BASELINE.json configs[3]); cfg5: 20 Hz replan loop of start/goal pairs (configs[4])")
-    ap.add_argument("--map-queries", type=int, default=16, help="cfg4: maps built both locally and row-sharded")
+    ap.add_argument("--map-queries", type=int, default=16, help="cfg4 --full: maps built both locally and row-sharded")
     ap.add_argument("--pairs", type=int, default=64, help="cfg5: start/goal pairs in total, dealt over the ranks")
     ap.add_argument("--generator", choices=("mt19937", "pcg64"), default="mt19937",
                     help="cfg3/cfg4 inputs: SURVEY.md §8d's std::mt19937 draws (the survey's reference runs) or "
                          "round 1's numpy PCG64 draws")
     ap.add_argument("--relaxed-delta", type=float, default=0.25, help="relaxed mode: frontier width (m)")
     ap.add_argument("--relaxed-weight", type=float, default=1.35, help="relaxed mode: heuristic weight (the library default)")
-    ap.add_argument("--no-relaxed", action="store_true", help="cfg5: skip the relaxed-mode comparison")
+    ap.add_argument("--no-relaxed", action="store_true", help="cfg5 --full: skip the relaxed-mode comparison")
     ap.add_argument("--relaxed-batch-nodes", type=int, default=1 << 16,
                     help="relaxed batch: node capacity per search (hastar_relaxed_opts.max_nodes)")
     ap.add_argument("--relaxed-reverse-cost", type=float, default=1.5,
                     help="relaxed batch leg: also run it with the reversing model at this reverse cost (0: skip)")
     ap.add_argument("--relaxed-gear-cost", type=float, default=1.0, help="... and this gear-change cost (m)")
     ap.add_argument("--relaxed-batch", type=int, default=4096,
-                    help="cfg3/cfg4: queries of the batch also planned in one relaxed call (query rate)")
+                    help="cfg3/cfg4 --full: queries of the batch also planned in one relaxed call (query rate)")
     ap.add_argument("--dump-timings", default=None,
-                    help="write every search's start/end/slot of the last timed step and of the cold-order "
+                    help="implies --full: write every search's start/end/slot of the last timed step and of the cold-order "
                          "step (npz) to this path")
     ap.add_argument("--no-deal", action="store_true",
                     help="cfg3/cfg4: contiguous query blocks per rank instead of the predicted-cost deal")
@@ -226,6 +276,8 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: exercises the launcher, sharding and reductions only (CPU rehearsal)")
     args = ap.parse_args(argv)
+    if args.parity_all or args.dump_timings:  # both read legs that only the full run has
+        args.full = True
     if args.grid is None:
         args.grid = 2048 if args.workload == "cfg4" else 1024
     if args.max_pops is None:
@@ -276,7 +328,9 @@ def main():
     if args.workload == "cfg5":
         return run_cfg5(args, gpu, dist, torch, rank, world, device)
     B = args.batch
-    map_build = map_build_phase(args, gpu, dist, torch, rank, world, device) if args.workload == "cfg4" else None
+    full = args.full
+    map_build = (map_build_phase(args, gpu, dist, torch, rank, world, device)
+                 if args.workload == "cfg4" and full else None)
     # every rank derives the same predicted costs of all world * B queries from their inputs
     # (no exchange); the deal balances predicted cost and orders each rank's batch by it
     t_pred = time.perf_counter()
@@ -317,13 +371,15 @@ def main():
     cold_s = time.perf_counter() - t0
     cold_handoffs = planners[0].handoffs()
     # what bounded the cold step: its last-ending searches (start, end, slot, pops), host-side
-    cold_t = np.array([p.timing() for p in planners], dtype=np.float64) if rank == 0 else None
+    cold_t = np.array([p.timing() for p in planners], dtype=np.float64) if rank == 0 and full else None
     progress("cold first step done")
     # the first step's outcome of a stratified sample (every 64th query and the 8 with the most
     # pops), paths included, for the bit-exact check against the oracle after the timed region
     # (host-side bookkeeping of the bench, outside the step's time)
-    strat = sorted(set(range(0, B, 64)) | set(np.argsort(-r0.stats["pops"], kind="stable")[:8].tolist()))
-    cold_sample = {i: r0.result(i) for i in strat} if (rank == 0 and not args.no_cpu_baseline) else None
+    cold_sample = None
+    if rank == 0 and full and not args.no_cpu_baseline:
+        strat = sorted(set(range(0, B, 64)) | set(np.argsort(-r0.stats["pops"], kind="stable")[:8].tolist()))
+        cold_sample = {i: r0.result(i) for i in strat}
     cold_all = None
     if rank == 0 and args.parity_all:  # every query's outcome, paths as digests of their bits
         cold_all = (r0.stats.copy(), r0.cost.copy(), r0.ok.copy(),
@@ -373,50 +429,53 @@ def main():
         pool = balance["pool"]  # the library splits a batch over 4x the CU count (hastar_capi.cpp batch_shape)
         split_launch = (os.environ.get("HASTAR_SPLIT", "1") != "0" and pool["head_cus"] > 0
                         and B > 4 * (pool["resident_slots"] // max(pool["waves_per_cu"], 1)))
-        timings = {"qids": np.asarray(qids), "pops": last.stats["pops"].copy(),
-                   "astar_pops": last.stats["astar_pops"].copy(),
-                   "warm": np.array([p.timing() for p in planners], dtype=np.float64)}
         progress("timed steps done")
-        # the last timed replan of the same stratified sample, paths included, for the oracle's
-        # replay of the whole call sequence (the node map's f values persist across reset, so a
-        # later replan is not the first one again)
-        last_sample = {i: last.result(i) for i in cold_sample} if cold_sample is not None else None
-        vel_prof = velocity_profile_phase(gpu, last, device, vels)  # before any other find_path
-        # the outcome arrays of the last timed step outlive the later steps on the same buffers
-        # (paths are not kept: only the velocity phase above reads them)
-        last = gpu.BatchResult(last.cost.copy(), last.ok.copy(), last.lens.copy(), None, None,
-                               last.stats.copy(), last.kernel_ms)
-        # a batch of fresh queries on a warm device: no longest-first history (every cost hint
-        # cleared), arenas already allocated — the library orders the queue by its cold key
-        for p in planners:
-            p.set_cost_hint(0)
-        torch.cuda.synchronize(device)
-        t0 = time.perf_counter()
-        rc = step()
-        cold_order_s = time.perf_counter() - t0
-        if args.dump_timings:
-            timings["cold_order"] = np.array([p.timing() for p in planners], dtype=np.float64)
-            np.savez(args.dump_timings, **timings)
-        cold_order = {"value": float(rc.stats["pops"].sum()) / cold_order_s, "ms": cold_order_s * 1e3,
-                      "note": "a step with every planner's cost hint cleared (no longest-first history) on an "
-                              "initialised device: the library orders the queue by its cold key"}
-        # latency queries: the survey's first seeds (query ids 0, 1, ..) where this rank has them
-        pos = {q: i for i, q in enumerate(qids)}
-        lat_ids = [pos[q] for q in range(args.latency_queries) if q in pos]
-        lat_ids += [i for i in range(B) if i not in lat_ids][:max(0, min(args.latency_queries, B) - len(lat_ids))]
-        lat = []
-        for i in lat_ids:  # single-query plan latency (the second half of the metric)
-            planners[i].reset()
-            _, kms = gpu.find_path_batch([planners[i]], [vels[i]], [starts[i]], cap=8192)
-            lat.append(kms)
-        # the batch's longest search alone (its latency bounds the step)
-        li = int(np.argmax(last.stats["pops"]))
-        longest = {"query": qids[li], "pops": int(last.stats["pops"][li])}
-        planners[li].reset()
-        _, longest["gpu_ms_alone"] = gpu.find_path_batch([planners[li]], [vels[li]], [starts[li]], cap=8192)
-        progress("latency queries done")
-        relaxed = relaxed_latency_phase(gpu, planners, vels, starts, last, lat_ids + [li], qids, args,
-                                        lat + [longest["gpu_ms_alone"]], B / (ms_per_step * 1e-3))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
+        if full:
+            timings = {"qids": np.asarray(qids), "pops": last.stats["pops"].copy(),
+                       "astar_pops": last.stats["astar_pops"].copy(),
+                       "warm": np.array([p.timing() for p in planners], dtype=np.float64)}
+            # the last timed replan of the same stratified sample, paths included, for the oracle's
+            # replay of the whole call sequence (the node map's f values persist across reset, so a
+            # later replan is not the first one again)
+            last_sample = {i: last.result(i) for i in cold_sample} if cold_sample is not None else None
+            vel_prof = velocity_profile_phase(gpu, last, device, vels)  # before any other find_path
+            # the outcome arrays of the last timed step outlive the later steps on the same buffers
+            # (paths are not kept: only the velocity phase above reads them)
+            last = gpu.BatchResult(last.cost.copy(), last.ok.copy(), last.lens.copy(), None, None,
+                                   last.stats.copy(), last.kernel_ms)
+            # a batch of fresh queries on a warm device: no longest-first history (every cost hint
+            # cleared), arenas already allocated — the library orders the queue by its cold key
+            for p in planners:
+                p.set_cost_hint(0)
+            torch.cuda.synchronize(device)
+            t0 = time.perf_counter()
+            rc = step()
+            cold_order_s = time.perf_counter() - t0
+            if args.dump_timings:
+                timings["cold_order"] = np.array([p.timing() for p in planners], dtype=np.float64)
+                np.savez(args.dump_timings, **timings)
+            cold_order = {"value": float(rc.stats["pops"].sum()) / cold_order_s, "ms": cold_order_s * 1e3,
+                          "note": "a step with every planner's cost hint cleared (no longest-first history) on an "
+                                  "initialised device: the library orders the queue by its cold key"}
+            # latency queries: the survey's first seeds (query ids 0, 1, ..) where this rank has them
+            pos = {q: i for i, q in enumerate(qids)}
+            lat_ids = [pos[q] for q in range(args.latency_queries) if q in pos]
+            lat_ids += [i for i in range(B) if i not in lat_ids][:max(0, min(args.latency_queries, B) - len(lat_ids))]
+            lat = []
+            for i in lat_ids:  # single-query plan latency (the second half of the metric)
+                planners[i].reset()
+                _, kms = gpu.find_path_batch([planners[i]], [vels[i]], [starts[i]], cap=8192)
+                lat.append(kms)
+            # the batch's longest search alone (its latency bounds the step)
+            li = int(np.argmax(last.stats["pops"]))
+            longest = {"query": qids[li], "pops": int(last.stats["pops"][li])}
+            planners[li].reset()
+            _, longest["gpu_ms_alone"] = gpu.find_path_batch([planners[li]], [vels[li]], [starts[li]], cap=8192)
+            progress("latency queries done")
+            relaxed = relaxed_latency_phase(gpu, planners, vels, starts, last, lat_ids + [li], qids, args,
+                                            lat + [longest["gpu_ms_alone"]], B / (ms_per_step * 1e-3))
         traffic = None
         pmc = ROOT / "profiles" / "pmc_search_summary.json"
         if pmc.exists():
@@ -436,6 +495,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": full,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "weak",
@@ -459,10 +519,6 @@ def main():
                                         "queue by its cold key: boxes near the start-goal route, hastar.h "
                                         "hastar_set_cost_hint); the device pool was reserved at setup "
                                         "(hastar_reserve, setup_split_s.reserve_s)"},
-            "cold_order_step": cold_order,
-            "plan_latency_ms": {"gpu_median": float(np.median(lat)) if lat else None, "queries": [qids[i] for i in lat_ids],
-                                "gpu": lat},
-            "longest_query": longest,
             "step_balance": balance,
             "pops_per_step": pops_all / args.steps,
             "success_rate": oks / (B * args.steps),
@@ -490,9 +546,14 @@ def main():
         }
         if map_build:
             out["map_build"] = map_build
-        out["velocity_profile"] = vel_prof
-        out["relaxed_mode"] = relaxed
-        if not args.no_cpu_baseline:
+        if full:
+            out["cold_order_step"] = cold_order
+            out["plan_latency_ms"] = {"gpu_median": float(np.median(lat)) if lat else None,
+                                      "queries": [qids[i] for i in lat_ids], "gpu": lat}
+            out["longest_query"] = longest
+            out["velocity_profile"] = vel_prof
+            out["relaxed_mode"] = relaxed
+        if full and not args.no_cpu_baseline:
             # the CPU sample runs the rank's queries in query-id order (a representative sample,
             # not the predicted-costliest head of the GPU batch), latency queries first
             sample = lat_ids + [i for i in np.argsort(qids, kind="stable") if i not in lat_ids]
@@ -817,6 +878,7 @@ def run_cfg5(args, gpu, dist, torch, rank, world, device):
     # every (pair, tick) outcome of the exact loop, warm-up ticks included, for the parity
     # readout against the oracle's replay of the same loop (cpu_baseline_cfg5)
     gpu_ticks = [[] for _ in pairs]
+    last_tick = [None]  # the latest tick's BatchResult (views `bufs`: valid until the next find_path)
 
     def step(timed):
         """One tick; returns (stats, kernel ms, successes, seconds of the exact tick).  When
@@ -828,14 +890,16 @@ def run_cfg5(args, gpu, dist, torch, rank, world, device):
         br = gpu.find_path_batch_arrays(planners, vels, starts, buffers=bufs)
         st = br.stats.copy()
         t_exact = time.perf_counter() - t0
-        for i in range(len(planners)):
-            gpu_ticks[i].append(tick_key(br.result(i)))
+        last_tick[0] = br
+        if args.full and not args.no_cpu_baseline:
+            for i in range(len(planners)):
+                gpu_ticks[i].append(tick_key(br.result(i)))
         if timed:  # the tick's slowest search (it bounds the tick): its pops and inner A* pops
             tm = np.array([p.timing() for p in planners], dtype=np.float64)
             j = int(np.argmax(tm[:, 1] - tm[:, 0]))
             slowest.append({"pair": int(ids[j]), "ms": float((tm[j, 1] - tm[j, 0]) * 1e-5), "pops": int(st["pops"][j]),
                             "astar_pops": int(st["astar_pops"][j])})
-        if timed and not args.no_relaxed and planners:
+        if timed and args.full and not args.no_relaxed and planners:
             t1 = time.perf_counter()
             rel, rms = gpu.find_path_batch(planners, vels, starts, cap=8192, relaxed=relaxed_opts)
             rx["wall_ms"].append((time.perf_counter() - t1) * 1e3)
@@ -871,13 +935,15 @@ def run_cfg5(args, gpu, dist, torch, rank, world, device):
     elapsed, pops_all = reduce_over_ranks(dist, elapsed, pops, f"cuda:{device}")
     out = None
     if rank == 0:
+        if args.dump_outputs and last_tick[0] is not None:
+            dump_outputs(args.dump_outputs, last_tick[0])
         avg_k = float(np.mean(kms))
         achieved = float(np.mean(alg)) / (avg_k * 1e-3) / 1e9
         out = {
             "metric": METRIC,
             "value": pops_all / elapsed, "unit": "expansions/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "warmup": args.warmup, "full": args.full, "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic (SURVEY.md §8d cfg5 generator; pair ids seed the boxes, goals and box velocities)",
             "config": {"workload": f"cfg5: {args.grid}x{args.grid}x{args.bins} grid, {args.obstacles} moving boxes, "
                                    f"{args.pairs} start/goal pairs in total replanned every 50 ms tick without reset",
@@ -903,7 +969,7 @@ def run_cfg5(args, gpu, dist, torch, rank, world, device):
                 "opts": relaxed_opts,
                 "note": "non-parity mode (hastar_find_path_relaxed_batch) on the same ticks' maps and starts as the "
                         "exact loop (rank 0); tick_ms = its find_path wall + the same batched upkeep"}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"], replay = cpu_baseline_cfg5(pairs, args.cpu_seconds, args.warmup + args.steps, args.warmup)
             out["parity_sample"] = cfg5_parity(gpu_ticks, replay, ids)
     if dist:

@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 R=/tmp/rp_$TAG
 rm -rf $R && mkdir -p $R
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/trace -o run -- python3 bench.py --warmup 2 --steps 3 > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/trace -o run -- python3 bench.py --full --warmup 2 --steps 3 > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 python3 tools/prof_summary.py trace $R/trace $OUT/trace_summary.json --warmup 2 --steps 3 || exit 1
 find $R/trace -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;

@@ -282,6 +282,53 @@ int hastar_velocity_profile_last_batch(int device, const hastar_velocity_params*
                                        const float* max_velocity_curr, const unsigned char* flags, float* velocity,
                                        unsigned char* feasible);
 
+/* ---- clearance field and path smoother (no reference counterpart: the
+ * reference returns the search's arcs as they are; BASELINE.json north_star names "Grid2D
+ * obstacle inflation").  Float planners only (no hastar64_* twin). ---- */
+#define HASTAR_CLEAR_NONE 0x7fffffff
+#define HASTAR_SMOOTH_MAX_POINTS 8192
+
+/* d2[p*N*N + i*N + j] = min over occupied cells (i', j') of planner p's map of
+ * (i - i')^2 + (j - j')^2, as int32: the exact squared Euclidean distance transform, in cells.
+ * "Occupied" is occ >= thr, the predicate of Grid3D.cpp:59,86.  HASTAR_CLEAR_NONE everywhere
+ * when the map has no occupied cell.  The grid border is not an obstacle.  dst is a DEVICE
+ * buffer on the planners' device.  The planners share one device and one N; HASTAR_EINVAL
+ * otherwise, or when 2 (N - 1)^2 does not fit int32 (N > 32768).  Returns after the fields
+ * are complete. */
+int hastar_clearance_field_batch(const hastar_handle* hs, int n, int* dst_device);
+
+/* Gradient smoother (Dolgov et al. 2010) over the clearance field: Jacobi gradient descent on
+ * J = w_smooth S + w_obs O + w_fid F with the step 1 / (32 w_smooth + 4 w_obs + 2 w_fid), then
+ * the result is blended back towards the input until the map and the vehicle accept it.
+ * The defaults are starting values, NOT measured ones: nothing has tuned them on a vehicle. */
+typedef struct hastar_smooth_opts {   /* NULL or 0 fields = defaults in brackets */
+  float w_smooth;   /* [1.0]  sum |x[i-1] - 2 x[i] + x[i+1]|^2 */
+  float w_obs;      /* [0.5]  sum (d_max - c(x[i]))^2 where c < d_max */
+  float w_fid;      /* [0.05] sum |x[i] - x0[i]|^2 */
+  float d_max;      /* [2.0 m] reach of the obstacle term */
+  int   iterations; /* [200], at most 4096 */
+  float kappa_max;  /* [largest of the planner's curv_abs] */
+  int   max_maps_in_flight; /* [as many maps as keep the pooled scratch, an N*N int32 field plus
+                               3 N*N int32 of column stacks per map, within 1 GiB] */
+} hastar_smooth_opts;
+/* A weight of 0 selects its default; a negative weight switches the term off (it counts as 0). */
+
+/* Path p = points [off[p], off[p+1]) of xyh, in the world frame and goal -> start order,
+ * as find_path returns them.  dir may be NULL and means all +1.
+ * Outputs: xyh_out/curv_out in the same packing; blend[p] in {1, .5, .25, .125, 0}: the
+ * output is x0 + blend (smoothed - x0), and 0 returns the input bit for bit;
+ * status[p] = 0, or HASTAR_ENOSPC with the path copied through unchanged when it has more
+ * than HASTAR_SMOOTH_MAX_POINTS points.  A path with fewer than 5 points is copied through
+ * with blend 0.  Points 0, 1, n-2, n-1 and every i with dir[i] != dir[i+1], with i-1 and i+1,
+ * never move and keep their heading; the other headings follow the direction of travel, and
+ * curv_out is the Menger curvature of the output points (the end points copy their neighbour).
+ * Host buffers in and out, like hastar_velocity_profile_batch.  hs[p] is the planner whose map
+ * and frame path p lives in; the planners share one device and one N.  A handle may repeat. */
+int hastar_smooth_paths_batch(const hastar_handle* hs, int n, const long long* off,
+                              const float* xyh, const float* curv, const signed char* dir,
+                              float* xyh_out, float* curv_out, float* blend, int* status,
+                              const hastar_smooth_opts* opts);
+
 /* Grid size N of the handle. */
 int hastar_grid_size(hastar_handle h);
 

@@ -67,6 +67,13 @@ double hastar_test_route_score(const float* boxes, int n, const float start[2], 
  * expansion index; workgroup b, wave w at [(b * 8 + w) * 4]) in pinned host memory, readable
  * while a launch runs; null unless HASTAR_RELAXED_PROGRESS was set before the first relaxed call. */
 const unsigned* hastar_debug_relaxed_progress(void);
+/* The planner's grid frame and map constants, so that a test can restate the smoother's
+ * world <-> grid transform from the library's own bits: {rot_c, rot_s, world_goal_x,
+ * world_goal_y, goal_x, goal_y, res, thr}. */
+int hastar_debug_frame(hastar_handle h, float out[8]);
+/* Device time of this thread's last hastar_clearance_field_batch / hastar_smooth_paths_batch:
+ * {ms in the clearance-field kernels, ms in the smoothing kernels} (HIP events). */
+int hastar_debug_smooth_ms(float out[2]);
 
 #ifdef __cplusplus
 }

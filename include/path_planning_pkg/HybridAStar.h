@@ -25,6 +25,8 @@
 //     (hastar_find_path_relaxed_batch).  That mode is NOT the reference's
 //     algorithm: its paths are valid and comparable in cost but not identical.  It keeps its
 //     heuristic field until reset() / update_goal(), as the reference keeps its A* memo.
+//   * extension, float only: smooth_path(path, curvature, blend) runs the gradient path
+//     smoother over the map's clearance field on find_path's output.
 #ifndef HYBRID_ASTAR
 #define HYBRID_ASTAR
 
@@ -182,6 +184,35 @@ class HybridAStar<float> {
       curvature.push_back(_curv[i]);
     }
     return {cost, ok != 0};
+  }
+  // extension (not in the reference, float only): smooth a path of this planner in place with
+  // the gradient smoother over the map's clearance field (hastar_smooth_paths_batch with its
+  // default options, every pose driven forward).  `path` and `curvature` are
+  // find_path's output and are overwritten; *blend receives the accepted blend factor (0: the
+  // input came back unchanged).  Returns false when nothing changed (blend 0, or a path longer
+  // than HASTAR_SMOOTH_MAX_POINTS).
+  bool smooth_path(std::vector<Vector3D<float>>& path, std::vector<float>& curvature, float* blend = nullptr) {
+    if (path.size() != curvature.size())
+      throw std::invalid_argument("HybridAStar::smooth_path: path and curvature differ in length");
+    const size_t n = path.size();
+    std::vector<float> in(3 * n), out(3 * n), kout(n);
+    for (size_t i = 0; i < n; ++i) {
+      in[3 * i] = path[i]._x;
+      in[3 * i + 1] = path[i]._y;
+      in[3 * i + 2] = path[i]._heading;
+    }
+    const long long off[2] = {0, (long long)n};
+    float b = 0.0f;
+    int status = 0;
+    check(hastar_smooth_paths_batch(&_h, 1, off, in.data(), curvature.data(), nullptr, out.data(), kout.data(), &b,
+                                    &status, nullptr));
+    if (blend) *blend = b;
+    if (status != 0 || b == 0.0f) return false;
+    for (size_t i = 0; i < n; ++i) {
+      path[i] = Vector3D<float>(out[3 * i], out[3 * i + 1], out[3 * i + 2]);
+      curvature[i] = kout[i];
+    }
+    return true;
   }
 
  private:

@@ -83,6 +83,20 @@ class HastarRelaxedOpts(C.Structure):
     ]
 
 
+class HastarSmoothOpts(C.Structure):
+    """hastar_smooth_opts (include/hastar.h): 0 selects a field's default; a negative weight
+    switches its term off."""
+    _fields_ = [
+        ("w_smooth", C.c_float),
+        ("w_obs", C.c_float),
+        ("w_fid", C.c_float),
+        ("d_max", C.c_float),
+        ("iterations", C.c_int),
+        ("kappa_max", C.c_float),
+        ("max_maps_in_flight", C.c_int),
+    ]
+
+
 class PlannerConfig:
     """Python-side planner configuration; owns the float arrays the struct points to."""
 

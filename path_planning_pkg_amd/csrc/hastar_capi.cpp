@@ -37,6 +37,7 @@
 #include "glibc_mathf.h"
 #include "hastar_kernels.h"
 #include "hastar_layout.h"
+#include "hastar_smooth.h"
 
 using namespace hastar;
 using gmath::g_atan2f;
@@ -257,6 +258,12 @@ struct DeviceCtx {
   size_t rfields_cap = 0;
   signed char* d_dir = nullptr;      // per-pose directions of a relaxed batch (hastar_find_path_relaxed_batch_dir)
   size_t dir_cap = 0;
+  // clearance field and smoother (hastar_smooth.hip): both grown on demand and kept
+  char* sm_pool = nullptr;           // clearance fields of a smoothing chunk, then the column stacks
+  size_t sm_pool_cap = 0;
+  char* sm_slab = nullptr;           // staged paths, tables and outputs of a call
+  size_t sm_slab_cap = 0;
+  hipEvent_t sm_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 // A larger arena that continues one parked search (hastar_find_path_batch).
@@ -3208,6 +3215,229 @@ int hastar_debug_closed_keys(hastar_handle h, int* out, int cap) {
     out[3 * i + 2] = (int)(k[i] & 0xffff);
   }
   return n;
+}
+
+// ------------------------------- clearance field and path smoother (hastar_smooth.hip) ---
+static thread_local float g_smooth_ms[2] = {0.0f, 0.0f};
+constexpr size_t kSmoothPoolBytes = (size_t)1 << 30;  // fields + column stacks of the maps in flight
+
+// a pooled device buffer of the smoother: grown on demand and kept (growth waits for the
+// stream, so no queued kernel still uses the old buffer)
+static int sm_grow(DeviceCtx& D, char** buf, size_t* cap, size_t bytes, const char* what) {
+  if (*cap >= bytes) return 0;
+  HIPCHK(hipStreamSynchronize(D.stream));
+  if (*buf) hipFree(*buf);
+  *buf = nullptr;
+  *cap = 0;
+  if (hipMalloc(reinterpret_cast<void**>(buf), bytes) != hipSuccess) {
+    *buf = nullptr;
+    return fail(HASTAR_ENOMEM, std::string(what) + ": scratch hipMalloc failed");
+  }
+  *cap = bytes;
+  return 0;
+}
+static int sm_events(DeviceCtx& D) {
+  for (hipEvent_t& e : D.sm_ev)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  return 0;
+}
+// the planners of one clearance / smoothing call: one device, one N that the field can hold
+static int sm_check_handles(const hastar_handle* hs, int n, const char* who) {
+  for (int p = 0; p < n; ++p) {
+    if (!hs[p]) return fail(HASTAR_EINVAL, std::string(who) + ": null handle");
+    if (hs[p]->dc != hs[0]->dc || hs[p]->desc.N != hs[0]->desc.N)
+      return fail(HASTAR_EINVAL, std::string(who) + ": the planners must share one device and one grid size");
+  }
+  if (hs[0]->desc.N > EDT_MAX_N)
+    return fail(HASTAR_EINVAL, std::string(who) + ": 2 (N - 1)^2 does not fit int32");
+  return 0;
+}
+// maps whose field and column stacks (16 N^2 bytes) fit the pooled scratch
+static int sm_maps_in_pool(size_t NN) {
+  return (int)std::min<size_t>(std::max<size_t>(kSmoothPoolBytes / (16 * NN), 1), 32768);
+}
+
+int hastar_clearance_field_batch(const hastar_handle* hs, int n, int* dst) {
+  if (!hs || n < 0 || (n > 0 && !dst)) return fail(HASTAR_EINVAL, "clearance_field: null argument");
+  if (n == 0) return HASTAR_OK;
+  if (int rc = sm_check_handles(hs, n, "clearance_field")) return rc;
+  HIPCHK(hipSetDevice(hs[0]->device));
+  DeviceCtx& DC = *hs[0]->dc;
+  std::lock_guard<std::mutex> lk(DC.mu);
+  const int N = hs[0]->desc.N;
+  const size_t NN = (size_t)N * N;
+  const int chunk = std::min(n, sm_maps_in_pool(NN));
+  if (int rc = sm_grow(DC, &DC.sm_pool, &DC.sm_pool_cap, (size_t)chunk * 12 * NN, "clearance_field")) return rc;
+  if (int rc = sm_grow(DC, &DC.sm_slab, &DC.sm_slab_cap, align256((size_t)n * sizeof(EdtMap)), "clearance_field"))
+    return rc;
+  if (int rc = sm_events(DC)) return rc;
+  std::vector<EdtMap> maps(n);
+  for (int p = 0; p < n; ++p) maps[p] = EdtMap{hs[p]->desc.occ, dst + (size_t)p * NN, hs[p]->desc.thr, 0};
+  hipStream_t st = DC.stream;
+  EdtMap* d_maps = reinterpret_cast<EdtMap*>(DC.sm_slab);
+  HIPCHK(hipMemcpyAsync(d_maps, maps.data(), (size_t)n * sizeof(EdtMap), hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(DC.sm_ev[0], st));
+  for (int c0 = 0; c0 < n; c0 += chunk)
+    HIPCHK(launch_edt(d_maps + c0, std::min(chunk, n - c0), N, reinterpret_cast<int*>(DC.sm_pool), st));
+  HIPCHK(hipEventRecord(DC.sm_ev[1], st));
+  HIPCHK(hipStreamSynchronize(st));
+  g_smooth_ms[1] = 0.0f;
+  HIPCHK(hipEventElapsedTime(&g_smooth_ms[0], DC.sm_ev[0], DC.sm_ev[1]));
+  return HASTAR_OK;
+}
+
+int hastar_smooth_paths_batch(const hastar_handle* hs, int n, const long long* off, const float* xyh,
+                              const float* curv, const signed char* dir, float* xyh_out, float* curv_out,
+                              float* blend, int* status, const hastar_smooth_opts* opts) {
+  if (n < 0 || (n > 0 && (!hs || !off || !xyh || !curv || !xyh_out || !curv_out || !blend || !status)))
+    return fail(HASTAR_EINVAL, "smooth_paths: null argument");
+  if (n == 0) return HASTAR_OK;
+  if (off[0] != 0) return fail(HASTAR_EINVAL, "smooth_paths: off[0] must be 0");
+  for (int p = 0; p < n; ++p)
+    if (off[p + 1] < off[p] || off[p + 1] - off[p] > 0x7fffffffll)
+      return fail(HASTAR_EINVAL, "smooth_paths: offsets of path " + std::to_string(p));
+  if (int rc = sm_check_handles(hs, n, "smooth_paths")) return rc;
+  for (int p = 0; p < n; ++p)
+    if (!hs[p]->goal_set) return fail(HASTAR_EINVAL, "smooth_paths: update_goal must be called first");
+  // options: 0 selects a default, a negative weight switches its term off
+  const hastar_smooth_opts o = opts ? *opts : hastar_smooth_opts{};
+  auto weight = [](float w, float dflt) { return w == 0.0f ? dflt : (w < 0.0f ? 0.0f : w); };
+  const float ws = weight(o.w_smooth, 1.0f), wo = weight(o.w_obs, 0.5f), wf = weight(o.w_fid, 0.05f);
+  const float d_max = o.d_max == 0.0f ? 2.0f : o.d_max;
+  const int iters = o.iterations == 0 ? 200 : o.iterations;
+  if (!(d_max > 0.0f) || iters < 0 || iters > 4096 || o.max_maps_in_flight < 0 || o.kappa_max < 0.0f ||
+      !(ws >= 0.0f && wo >= 0.0f && wf >= 0.0f))
+    return fail(HASTAR_EINVAL, "smooth_paths: option out of range");
+  const float lip = (32.0f * ws + 4.0f * wo) + 2.0f * wf;  // Lipschitz bound of the three gradients
+  if (!(lip > 0.0f)) return fail(HASTAR_EINVAL, "smooth_paths: every weight is off");
+  const SmoothParams sp{ws + ws, wo + wo, wf + wf, 1.0f / lip, d_max, iters};
+
+  HIPCHK(hipSetDevice(hs[0]->device));
+  DeviceCtx& DC = *hs[0]->dc;
+  std::lock_guard<std::mutex> lk(DC.mu);
+  const int N = hs[0]->desc.N;
+  const size_t NN = (size_t)N * N;
+  const size_t pts = (size_t)off[n];
+  g_smooth_ms[0] = g_smooth_ms[1] = 0.0f;
+  if (pts == 0) {
+    for (int p = 0; p < n; ++p) blend[p] = 0.0f, status[p] = 0;
+    return HASTAR_OK;
+  }
+  const int in_flight = o.max_maps_in_flight > 0 ? std::min(o.max_maps_in_flight, 32768) : sm_maps_in_pool(NN);
+
+  // chunks of consecutive paths whose distinct planners number at most in_flight
+  struct Chunk { int p0, p1, m0, m1, max_points; };
+  std::vector<Chunk> chunks;
+  std::vector<SmoothMap> smaps;
+  std::vector<EdtMap> emaps;
+  std::vector<int> map_of(n), pool_slot;
+  {
+    std::unordered_map<hastar_handle, int> slot;
+    Chunk c{0, 0, 0, 0, 0};
+    for (int p = 0; p < n; ++p) {
+      auto it = slot.find(hs[p]);
+      if (it == slot.end() && (int)slot.size() == in_flight) {
+        c.p1 = p;
+        c.m1 = (int)smaps.size();
+        chunks.push_back(c);
+        c = Chunk{p, p, c.m1, c.m1, 0};
+        slot.clear();
+      }
+      it = slot.find(hs[p]);
+      if (it == slot.end()) {
+        const int s = (int)slot.size();  // the chunk's field number s sits at pool + s * NN ints
+        const PlannerDev& D = hs[p]->desc;
+        float kmax = o.kappa_max;
+        if (kmax == 0.0f)
+          for (float k : hs[p]->curv_abs) kmax = std::max(kmax, k);
+        pool_slot.push_back(s);  // the field pointers are set once the pool is there
+        smaps.push_back(SmoothMap{D.occ, nullptr, N, D.res, D.thr, D.rot_c, D.rot_s, D.world_goal_x, D.world_goal_y,
+                                  D.goal_x, D.goal_y, kmax});
+        emaps.push_back(EdtMap{D.occ, nullptr, D.thr, 0});
+        it = slot.emplace(hs[p], (int)smaps.size() - 1).first;
+      }
+      map_of[p] = it->second;
+      c.max_points = (int)std::max<long long>(c.max_points, std::min<long long>(off[p + 1] - off[p], HASTAR_SMOOTH_MAX_POINTS));
+    }
+    c.p1 = n;
+    c.m1 = (int)smaps.size();
+    chunks.push_back(c);
+  }
+  int pool_maps = 0;
+  for (const Chunk& c : chunks) pool_maps = std::max(pool_maps, c.m1 - c.m0);
+  if (int rc = sm_grow(DC, &DC.sm_pool, &DC.sm_pool_cap, (size_t)pool_maps * 16 * NN, "smooth_paths")) return rc;
+  int* fields = reinterpret_cast<int*>(DC.sm_pool);
+  int* stacks = fields + (size_t)pool_maps * NN;
+  for (size_t m = 0; m < smaps.size(); ++m) {
+    emaps[m].dst = fields + (size_t)pool_slot[m] * NN;
+    smaps[m].d2 = emaps[m].dst;
+  }
+
+  const size_t M = smaps.size();
+  const size_t b_off = align256((n + 1) * sizeof(long long)), b_xyh = align256(3 * pts * sizeof(float)),
+               b_pt = align256(pts * sizeof(float)), b_dir = align256(pts), b_g0 = align256(2 * pts * sizeof(float)),
+               b_n = align256(n * sizeof(float)), b_sm = align256(M * sizeof(SmoothMap)),
+               b_em = align256(M * sizeof(EdtMap));
+  const size_t total = b_off + 2 * b_xyh + 2 * b_pt + b_dir + b_g0 + 3 * b_n + b_sm + b_em;
+  if (int rc = sm_grow(DC, &DC.sm_slab, &DC.sm_slab_cap, total + total / 2, "smooth_paths")) return rc;
+  if (int rc = sm_events(DC)) return rc;
+  char* q = DC.sm_slab;
+  auto take = [&](size_t b) { char* r = q; q += b; return r; };
+  long long* d_off = reinterpret_cast<long long*>(take(b_off));
+  float* d_xyh = reinterpret_cast<float*>(take(b_xyh));
+  float* d_xyh_out = reinterpret_cast<float*>(take(b_xyh));
+  float* d_curv = reinterpret_cast<float*>(take(b_pt));
+  float* d_curv_out = reinterpret_cast<float*>(take(b_pt));
+  signed char* d_dir = reinterpret_cast<signed char*>(take(b_dir));
+  float* d_g0 = reinterpret_cast<float*>(take(b_g0));
+  float* d_blend = reinterpret_cast<float*>(take(b_n));
+  int* d_status = reinterpret_cast<int*>(take(b_n));
+  int* d_map_of = reinterpret_cast<int*>(take(b_n));
+  SmoothMap* d_smaps = reinterpret_cast<SmoothMap*>(take(b_sm));
+  EdtMap* d_emaps = reinterpret_cast<EdtMap*>(take(b_em));
+  hipStream_t st = DC.stream;
+  HIPCHK(hipMemcpyAsync(d_off, off, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_xyh, xyh, 3 * pts * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_curv, curv, pts * sizeof(float), hipMemcpyHostToDevice, st));
+  if (dir) HIPCHK(hipMemcpyAsync(d_dir, dir, pts, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_map_of, map_of.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_smaps, smaps.data(), M * sizeof(SmoothMap), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_emaps, emaps.data(), M * sizeof(EdtMap), hipMemcpyHostToDevice, st));
+  for (const Chunk& c : chunks) {  // clearance fields of the chunk's planners, then one smoothing launch
+    HIPCHK(hipEventRecord(DC.sm_ev[0], st));
+    HIPCHK(launch_edt(d_emaps + c.m0, c.m1 - c.m0, N, stacks, st));
+    HIPCHK(hipEventRecord(DC.sm_ev[1], st));
+    HIPCHK(launch_smooth(d_smaps, d_map_of, d_off, c.p0, c.p1 - c.p0, c.max_points, d_xyh, d_curv,
+                         dir ? d_dir : nullptr, d_xyh_out, d_curv_out, d_g0, d_blend, d_status, sp, st));
+    HIPCHK(hipEventRecord(DC.sm_ev[2], st));
+    HIPCHK(hipStreamSynchronize(st));  // the next chunk reuses the pool and the events
+    float a = 0.0f, b = 0.0f;
+    HIPCHK(hipEventElapsedTime(&a, DC.sm_ev[0], DC.sm_ev[1]));
+    HIPCHK(hipEventElapsedTime(&b, DC.sm_ev[1], DC.sm_ev[2]));
+    g_smooth_ms[0] += a;
+    g_smooth_ms[1] += b;
+  }
+  HIPCHK(hipMemcpyAsync(xyh_out, d_xyh_out, 3 * pts * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(curv_out, d_curv_out, pts * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(blend, d_blend, n * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(status, d_status, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return HASTAR_OK;
+}
+
+int hastar_debug_frame(hastar_handle h, float out[8]) {
+  if (!h || !out) return fail(HASTAR_EINVAL, "null argument");
+  const PlannerDev& D = h->desc;
+  const float v[8] = {D.rot_c, D.rot_s, D.world_goal_x, D.world_goal_y, D.goal_x, D.goal_y, D.res, D.thr};
+  std::memcpy(out, v, sizeof(v));
+  return HASTAR_OK;
+}
+
+int hastar_debug_smooth_ms(float out[2]) {
+  if (!out) return fail(HASTAR_EINVAL, "null argument");
+  out[0] = g_smooth_ms[0];
+  out[1] = g_smooth_ms[1];
+  return HASTAR_OK;
 }
 
 }  // extern "C"

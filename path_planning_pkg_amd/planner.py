@@ -13,7 +13,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .capi import HastarRelaxedOpts, HastarStats, PlannerConfig, fptr, iptr
+from .capi import HastarRelaxedOpts, HastarSmoothOpts, HastarStats, PlannerConfig, fptr, iptr
 
 import os
 
@@ -22,6 +22,8 @@ _lib = None
 
 HASTAR_ENOSPC = -28
 HASTAR_EOVERFLOW = -75
+HASTAR_CLEAR_NONE = 0x7fffffff
+HASTAR_SMOOTH_MAX_POINTS = 8192
 
 
 class HastarError(RuntimeError):
@@ -108,6 +110,11 @@ def load_library():
     L.hastar_update_boxes_batch.argtypes = [hp, C.c_int, fp, fp, ip, C.c_float]
     L.hastar_velocity_profile_last_batch.argtypes = [C.c_int, C.POINTER(HastarVelocityParams), C.c_int, fp, fp,
                                                      C.POINTER(C.c_ubyte), fp, C.POINTER(C.c_ubyte)]
+    L.hastar_clearance_field_batch.argtypes = [hp, C.c_int, C.c_void_p]
+    L.hastar_smooth_paths_batch.argtypes = [hp, C.c_int, C.POINTER(C.c_longlong), fp, fp, C.c_void_p, fp, fp, fp, ip,
+                                            C.POINTER(HastarSmoothOpts)]
+    L.hastar_debug_frame.argtypes = [vp, fp]
+    L.hastar_debug_smooth_ms.argtypes = [fp]
     _lib = L
     return L
 
@@ -312,6 +319,25 @@ class HybridAStar:
         """Install a whole field (device buffer, N x N) as the relaxed mode's heuristic (used by
         relaxed calls with reuse_heuristic=1, h_coarse=1 until reset / update_goal)."""
         _check(load_library().hastar_relaxed_set_field(self.h, C.c_void_p(int(src_ptr))))
+
+    # ---- clearance field and path smoother (include/hastar.h; DESIGN.md §4.7)
+    def clearance_field(self, dst_ptr):
+        """Write the N x N int32 squared distance (in cells) to the nearest occupied cell to the
+        device buffer at `dst_ptr` (row i = x cell; HASTAR_CLEAR_NONE in a map without occupied
+        cells).  Synchronous."""
+        clearance_field_batch([self], dst_ptr)
+
+    def smooth_path(self, path, curv, dir=None, **opts):
+        """Smooth one path of this planner (hastar_smooth_paths_batch): returns (path, curvature,
+        blend, status).  opts: hastar_smooth_opts fields."""
+        P, K, b, st = smooth_paths_batch([self], [path], [curv], None if dir is None else [dir], **opts)
+        return P[0], K[0], float(b[0]), int(st[0])
+
+    def frame(self):
+        """hastar_debug_frame: rot_c, rot_s, world_goal_x, world_goal_y, goal_x, goal_y, res, thr."""
+        out = np.zeros(8, np.float32)
+        _check(load_library().hastar_debug_frame(self.h, fptr(out)))
+        return out
 
     # HybridAStar::find_path (HybridAStar.cpp:68-88)
     def find_path(self, vel_init, start, cap=4096):
@@ -632,6 +658,61 @@ def find_path_batch(planners, vels, starts, cap=4096, relaxed=None):
         if relaxed is not None and k <= cap:  # each pose's direction of travel (+1 / -1)
             out[-1]["direction"] = dirs[i, :k].copy()
     return out, ms
+
+
+def clearance_field_batch(planners, dst_ptr):
+    """hastar_clearance_field_batch: planner p's N x N int32 field at dst_ptr + p * N * N * 4
+    (a device buffer on the planners' device, e.g. a torch tensor's data_ptr()).  Synchronous."""
+    hs, n = _handles(planners)
+    _check(load_library().hastar_clearance_field_batch(hs, n, C.c_void_p(int(dst_ptr))))
+
+
+def smooth_opts(**opts):
+    """hastar_smooth_opts from keyword arguments.  The C struct reads 0 as "default", so a weight
+    given here as 0 is passed as -1 ("term off"), which is what the caller wrote."""
+    o = dict(opts)
+    for k in ("w_smooth", "w_obs", "w_fid"):
+        if k in o and o[k] == 0:
+            o[k] = -1.0
+    return HastarSmoothOpts(**o)
+
+
+def smooth_paths_batch(planners, paths, curvs, dirs=None, **opts):
+    """hastar_smooth_paths_batch: paths[p] (k_p x 3, world frame, goal -> start as find_path
+    returns it) lives in planners[p]'s map and frame; dirs[p] its per-pose directions (+1 / -1) or
+    None.  Returns (paths, curvatures, blend f32[n], status i32[n])."""
+    hs, n = _handles(planners)
+    xyh = [_f32(p, (-1, 3)) for p in paths]
+    cv = [_f32(c) for c in curvs]
+    lens = np.array([len(p) for p in xyh], np.int64)
+    if len(xyh) != n or len(cv) != n or any(len(c) != l for c, l in zip(cv, lens)):
+        raise ValueError("smooth_paths_batch: planners, paths and curvatures differ in length")
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    X = np.ascontiguousarray(np.concatenate(xyh) if n else np.zeros((0, 3), np.float32))
+    K = np.ascontiguousarray(np.concatenate(cv) if n else np.zeros(0, np.float32))
+    D = None
+    if dirs is not None:
+        ds = [np.ones(l, np.int8) if d is None else np.ascontiguousarray(d, np.int8) for d, l in zip(dirs, lens)]
+        if len(ds) != n or any(len(d) != l for d, l in zip(ds, lens)):
+            raise ValueError("smooth_paths_batch: paths and directions differ in length")
+        D = np.ascontiguousarray(np.concatenate(ds) if n else np.zeros(0, np.int8))
+    Xo, Ko = np.empty_like(X), np.empty_like(K)
+    blend = np.zeros(n, np.float32)
+    status = np.zeros(n, np.int32)
+    o = smooth_opts(**opts)
+    _check(load_library().hastar_smooth_paths_batch(
+        hs, n, off.ctypes.data_as(C.POINTER(C.c_longlong)), fptr(X), fptr(K),
+        None if D is None else D.ctypes.data_as(C.c_void_p), fptr(Xo), fptr(Ko), fptr(blend), iptr(status),
+        C.byref(o)))
+    return ([Xo[off[i]:off[i + 1]] for i in range(n)], [Ko[off[i]:off[i + 1]] for i in range(n)], blend, status)
+
+
+def smooth_ms():
+    """(clearance-field ms, smoother ms) of this thread's last clearance / smoothing call."""
+    out = np.zeros(2, np.float32)
+    _check(load_library().hastar_debug_smooth_ms(fptr(out)))
+    return float(out[0]), float(out[1])
 
 
 def gpu_math(fn, a, b=None):

@@ -3,7 +3,9 @@ DESIGN.md §4.7).  Not an oracle of the reference (which has no smoother): it re
 library's documented arithmetic so that the device result can be compared to the bit.
 
   * edt_brute: the squared Euclidean distance transform by brute force in int64 (min over the
-    occupied cells, by broadcasting); edt_two_loops: the same with plain Python loops.
+    occupied cells, by broadcasting); edt_two_loops: the same with plain Python loops;
+    edt_separable: the same for maps too large for either (row distances, then a plain minimum
+    over the rows).
   * smooth_ref: the smoother, the blend and the accept rule in float32, one operation at a
     time in the kernel's order.  It takes the frame from hastar_debug_frame and the map from
     get_obstacles().
@@ -47,6 +49,30 @@ def edt_two_loops(occ, thr):
                 if d < best:
                     best = d
             out[i, j] = best
+    return out
+
+
+def edt_separable(occ, thr):
+    """The same field for large maps, O(N^3) whatever the occupancy: per row u the exact distance
+    g[u, j] along j to the row's nearest occupied cell (by broadcasting against the row's occupied
+    indices), then per output row i the minimum over u of (i - u)^2 + g[u, j]^2 in int64.  Rows
+    without an occupied cell carry a sentinel above every real value.  No scan, no envelope and
+    no separator: a different decomposition from the kernel's two passes."""
+    occ = np.asarray(occ, np.float32)
+    N = occ.shape[0]
+    m = occ >= f32(thr)
+    out = np.full((N, N), CLEAR_NONE, np.int64)
+    if not m.any():
+        return out
+    none = np.int64(1) << 40  # 2 (N - 1)^2 < 2^31 for every N the library takes
+    j = np.arange(N, dtype=np.int64)
+    g2 = np.full((N, N), none, np.int64)
+    for u in range(N):
+        jj = np.nonzero(m[u])[0].astype(np.int64)
+        if len(jj):
+            g2[u] = np.abs(j[:, None] - jj[None, :]).min(axis=1) ** 2
+    for i in range(N):
+        out[i] = (((i - j) ** 2)[:, None] + g2).min(axis=0)
     return out
 
 

@@ -41,6 +41,10 @@ int hastar_debug_astar_modes(hastar_handle h, long long* out2);
 /* Timing of the last search: {t_start, t_end} in s_memrealtime ticks (100 MHz, chip-wide
  * clock) and the slot (persistent wavefront) that ran it. */
 int hastar_debug_timing(hastar_handle h, unsigned long long* out3);
+/* Samples of the analytic shot (Dubins or Reeds-Shepp) at the head of the last search's path:
+ * poses 0 .. *out - 1 of the returned path are the shot, sample 0 (the shooter) last; 0 when a
+ * goal node ended the search.  HASTAR_EINVAL without a search result. */
+int hastar_debug_shot_len(hastar_handle h, int* out);
 /* Where the last search ran: XCC_ID << 16 | HW_ID[15:0] (wave, SIMD, pipe, CU, SH, SE fields) of
  * its wavefront at the end of the search. */
 int hastar_debug_hw_id(hastar_handle h, int* out);

@@ -1044,6 +1044,11 @@ int orc_find_path(void* h, float vel, const float start[3], float* xyh, float* c
   }
   return 0;
 }
+// Samples of the Dubins shot at the head of the last find_path's path (0: a goal node ended it).
+int orc_shot_len(void* h) {
+  auto* P = static_cast<OP*>(h);
+  return P->shot_ok ? (int)P->shot_path.size() : 0;
+}
 // Closed-set keys (cx, cy, bin) of the last search, sorted; returns the count.
 int orc_closed_keys(void* h, int* out, int cap) {
   auto* P = static_cast<OP*>(h);

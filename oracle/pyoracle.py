@@ -48,6 +48,7 @@ def lib(lean=False):
         L.orc_apf_count.argtypes = [vp]
         L.orc_get_apf.argtypes = [vp, fp]
         L.orc_find_path.argtypes = [vp, C.c_float, fp, fp, fp, C.c_int, ip, fp, ip, C.POINTER(HastarStats), dp]
+        L.orc_shot_len.argtypes = [vp]
         L.orc_closed_keys.argtypes = [vp, ip, C.c_int]
         L.orc_motion_tables.restype = C.c_float
         L.orc_motion_tables.argtypes = [vp, fp, fp, fp, fp]
@@ -177,7 +178,8 @@ class OraclePlanner:
             raise RuntimeError(f"oracle find_path rc={rc} len={ln.value}")
         n = ln.value
         return dict(cost=cost.value, ok=bool(ok.value), path=xyh[:n].copy(), curvature=curv[:n].copy(),
-                    stats=st.as_dict(), wall_ms=wall.value)
+                    stats=st.as_dict(), wall_ms=wall.value,
+                    shot_len=int(self._L.orc_shot_len(self.h)) if ok.value else 0)
 
     # ---- the stand-alone AStar<float> on this planner's plain Grid2D (AStar.h)
     def astar_goal_start(self, goal, start):

@@ -3129,6 +3129,12 @@ int hastar_debug_timing(hastar_handle h, unsigned long long* out3) {
   return HASTAR_OK;
 }
 
+int hastar_debug_shot_len(hastar_handle h, int* out) {
+  if (!h || !out || !h->have_last) return fail(HASTAR_EINVAL, "no search result");
+  *out = (h->last.ok && h->last.via_shot) ? h->last.dubins_len : 0;
+  return HASTAR_OK;
+}
+
 int hastar_debug_hw_id(hastar_handle h, int* out) {
   if (!h || !out || !h->have_last) return fail(HASTAR_EINVAL, "no search result");
   *out = h->last.hw_id;

@@ -7,8 +7,11 @@
 // The algorithm is the published one (Reeds & Shepp 1990, formulas 8.1-8.11: the families CSC,
 // CCC, CCCC, CCSC and CCSCC under the time-flip / reflection / backwards symmetries, 44
 // candidates over 18 words).  oracle/reeds_shepp.py restates it in double precision and is
-// the checker (tests/test_reeds_shepp.py): every candidate the device returns must integrate to
-// the goal, and the device's shortest length must equal the restatement's to float precision.
+// the checker (tests/test_reeds_shepp.py checks the restatement itself, on the CPU).  The device
+// is checked in tests/test_gpu_relaxed.py (hastar_test_reeds_shepp: the word the device returns
+// must integrate to the goal, and its shortest length must equal the restatement's to float
+// precision) and in tests/test_gpu_relaxed_audit.py (every returned shot: its samples lie on
+// its own segments' curve, end at the goal, are the shortest word and cost what was reported).
 //
 // Wave mapping: a candidate is (family group g in 0..10, symmetry s in 0..3).  For the
 // heuristic of a successor group of gs >= 4 lanes, lane sub of the group takes symmetry sub & 3

@@ -90,6 +90,7 @@ def load_library():
     L.hastar_debug_cycles.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.hastar_debug_astar_modes.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.hastar_debug_timing.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+    L.hastar_debug_shot_len.argtypes = [vp, ip]
     L.hastar_debug_slots.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.hastar_debug_head_arenas.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.hastar_debug_hw_id.argtypes = [vp, ip]
@@ -477,6 +478,13 @@ class HybridAStar:
         out = (C.c_ulonglong * 3)()
         _check(load_library().hastar_debug_timing(self.h, out))
         return out[0], out[1], int(out[2])
+
+    def shot_len(self):
+        """Samples of the analytic shot at the head of the last search's path (poses
+        0 .. shot_len - 1, the shooter last); 0 when a goal node ended the search."""
+        v = C.c_int(0)
+        _check(load_library().hastar_debug_shot_len(self.h, C.byref(v)))
+        return int(v.value)
 
     def hw_id(self):
         """(XCC, CU, SE, SH, SIMD) of the wavefront that ran the last search (HW_REG_XCC_ID /

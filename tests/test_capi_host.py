@@ -27,6 +27,7 @@ def test_library_exports_declared_symbols():
     lib = C.CDLL(str(LIB_PATH))
     syms = declared_symbols()
     assert "hastar_create_f32" in syms and "hastar_find_path_batch" in syms and "hastar64_find_path" in syms
+    assert "hastar_debug_shot_len" in syms and "hastar_debug_timing" in syms
     missing = [s for s in syms if not hasattr(lib, s)]
     assert not missing, missing
 
@@ -84,6 +85,17 @@ def test_relaxed_entry_point_rejects_bad_arguments():
     assert rc == -22  # HASTAR_EINVAL
     rc = L.hastar_find_path_relaxed_batch_dir(None, 0, f, f, f, f, None, 1, i, f, i, None, None)
     assert rc == -22
+
+
+def test_shot_len_hook_needs_a_result():
+    """hastar_debug_shot_len answers HASTAR_EINVAL without a handle (and, like the other hooks of the
+    last search's record, without a search result), and the oracle exports its counterpart."""
+    from oracle import pyoracle
+    from path_planning_pkg_amd.planner import load_library
+    out = C.c_int(-1)
+    assert load_library().hastar_debug_shot_len(None, C.byref(out)) == -22
+    assert out.value == -1
+    assert hasattr(pyoracle.lib(), "orc_shot_len")
 
 
 def test_route_score_cold_order_key():
